@@ -12,14 +12,23 @@ its own 4 GiB shard -- the next 1 Mi blocks of one global region -- and
 checksums it with no data-path collective ("weak" scaling); the barrier and
 the max-over-ranks reduction are the benchmark contract, not part of the path.
 
-Rank 0 prints ONE compact JSON line (~2.5 KB, compact_line: the contract's
-keys, the headline roofline and cpu_baseline, and under "legs" each other
-leg's value, ms_per_step, frac, frac_of_measured, traffic ratio and
-bit_exact) and writes the full result below to the detail file
-(gpurun_out/bench_detail.json, --detail).  The legs of the full result
-(every BASELINE config that fits a GPU is measured in the same run, each
-timed outside the headline's timed region, with barrier + max over ranks at
-N > 1):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline needs: it fills the region, runs the W warm-up steps and the untimed
+ramp, times the K steps, and rank 0 prints ONE compact JSON line (the
+contract's keys -- metric, value, unit, ms_per_step, ... -- and the headline
+roofline from the timed steps' own kernel time).  --dump-outputs DIR also
+writes the CRCs the last timed step left (what a caller of
+priskv_crc32_blocks_dev receives) as DIR/crc.npy, float64 (every uint32 CRC
+exactly); the inputs are the same seeded pattern in every run, so two builds
+can be compared CRC for CRC.
+
+--full adds every other leg below and the parity checks (the line is then
+~2.5 KB, compact_line: under "legs" each other leg's value, ms_per_step,
+frac, frac_of_measured, traffic ratio and bit_exact) and writes the full
+result to the detail file (bench_out/bench_detail.json, --detail).  The legs
+of the full result (every BASELINE config that fits a GPU is measured in the
+same run, each timed outside the headline's timed region, with barrier + max
+over ranks at N > 1):
   sweep         configs[2]: 64 Ki x 64 KiB and 4 Ki x 1 MiB (4 GiB per GPU
                 each), device-resident, each with its kernel's roofline and
                 every block checked bit-exactly against the CPU oracle
@@ -118,7 +127,14 @@ def parse(argv=None):
                    help="the 4 GiB legs (64 KiB, 1 MiB, odd sizes) each allocate their own region instead of "
                         "re-filling the headline's (rounds 1-6)")
     p.add_argument("--detail", default=None,
-                   help="where the full result goes (default gpurun_out/bench_detail.json); stdout gets the compact line")
+                   help="where the full result goes (default with --full: bench_out/bench_detail.json; without: not "
+                        "written); stdout gets the compact line")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: per-launch statistics and the read roof, the parity checks, the sweep, "
+                        "odd, tib, streamed and cold legs and the CPU baseline (the --no-* options pick among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the CRCs of the last timed step to DIR/crc.npy (float64; a seeded sample with its "
+                        "block indices in DIR/crc_index.npy when they would exceed 64 MB)")
     return p.parse_args(argv)
 
 
@@ -281,6 +297,25 @@ def read_roof(B, region, bs, nb, stream, alg, k, rotate=0):
                                     "the plan's shape with progress priority 1/3), each ramped alike, order rotated "
                                     f"per leg; mean of {k} launches each (one event pair per launch)",
             "roof_launch_ms": st}
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # files of one run, .npy headers (128 B each) included
+
+
+def dump_outputs(dirname, crc, rank, world):
+    """The timed path's output -- this rank's uint32 CRCs, one per block, as
+    the last timed step left them -- as float64 (exact for every uint32) in
+    DIR/crc.npy (crc_rank<r>.npy at N > 1).  Beyond DUMP_MAX_BYTES per run a
+    fixed, seeded sample of the blocks, with their indices beside it."""
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    budget = DUMP_MAX_BYTES // world
+    if 128 + crc.size * 8 > budget:
+        keep = (budget - 2 * 128) // 16  # 8 bytes of CRC + 8 bytes of index per block
+        idx = np.sort(np.random.default_rng(SEED).choice(crc.size, size=keep, replace=False))
+        np.save(os.path.join(dirname, f"crc_index{tag}.npy"), idx.astype(np.float64))
+        crc = crc[idx]
+    np.save(os.path.join(dirname, f"crc{tag}.npy"), crc.astype(np.float64))
 
 
 class Bench:
@@ -553,7 +588,7 @@ def compact_line(full: dict, detail_path: str) -> dict:
     sources, notes, per-rank identity) is in the detail file."""
     rl = full.get("roofline", {})
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-                                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in full}
+                                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "full") if k in full}
     cfg = full.get("config", {})
     line["config"] = {k: cfg[k] for k in ("workload", "block_size", "nblocks_per_gpu", "parallelism", "kernel",
                                           "timed_launches") if k in cfg}
@@ -568,9 +603,10 @@ def compact_line(full: dict, detail_path: str) -> dict:
         mt = [v for v in cb.get("variants", []) if v.get("opt") == "-O2" and v.get("threads", 1) > 1]
         if mt:
             line["cpu_baseline"]["multithread"] = {"threads": mt[0]["threads"], "value": mt[0]["value"]}
-    par = full.get("parity", {})
-    line["parity"] = {k: par[k] for k in ("bit_exact", "bit_exact_vs_reference_build", "checked_blocks_per_rank")
-                      if k in par}
+    if "parity" in full:
+        par = full["parity"]
+        line["parity"] = {k: par[k] for k in ("bit_exact", "bit_exact_vs_reference_build", "checked_blocks_per_rank")
+                          if k in par}
     d = full.get("dist", {})
     line["dist"] = {k: d[k] for k in ("backend", "world_size", "distinct_devices", "rehearsal") if k in d}
     legs = {}
@@ -594,10 +630,12 @@ def compact_line(full: dict, detail_path: str) -> dict:
     if isinstance(cold, dict):
         legs["cold"] = ({"value": cold.get("value"), "ms": cold.get("ms"), "frac": cold.get("frac"),
                          "walked_value": cold.get("walked_value")} if "error" not in cold else {"error": cold["error"]})
-    line["legs"] = legs
+    if legs or full.get("full", True):
+        line["legs"] = legs
     if "cold_ms" in full:
         line["cold_ms"] = full["cold_ms"]
-    line["detail"] = detail_path
+    if detail_path is not None:
+        line["detail"] = detail_path
     return line
 
 
@@ -642,7 +680,8 @@ def main():
     from priskv_amd import CrcContext, as_u32
     from priskv_amd.shard import shard_blocks, shard_word_offset
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import _oracle as O
+    if args.full:
+        import _oracle as O
 
     bs, nb, desc = CONFIGS[args.config]
     if args.block_size:
@@ -676,14 +715,18 @@ def main():
 
     elapsed_max, kernel_ms = B.timed(step, stream, args.steps)
     walls["headline"] = time.perf_counter() - t_leg
+    # what the last timed step computed, before anything else writes `out`
+    dumped = as_u32(out) if args.dump_outputs else None
 
-    # a second window, one event pair per launch (median / min), then the
-    # read roof of the same access pattern over the same region
-    t_leg = time.perf_counter()
     alg_bytes = nb * (bs + 4)  # block read + 4-byte CRC written
-    lstats = launch_stats(per_launch_ms(step, stream, torch, args.steps))
-    roof = read_roof(B, region, bs, nb, stream, alg_bytes, args.steps) if bs % 4096 == 0 else None
-    walls["launch_stats_and_roof"] = time.perf_counter() - t_leg
+    lstats = roof = None
+    if args.full:
+        # a second window, one event pair per launch (median / min), then the
+        # read roof of the same access pattern over the same region
+        t_leg = time.perf_counter()
+        lstats = launch_stats(per_launch_ms(step, stream, torch, args.steps))
+        roof = read_roof(B, region, bs, nb, stream, alg_bytes, args.steps) if bs % 4096 == 0 else None
+        walls["launch_stats_and_roof"] = time.perf_counter() - t_leg
 
     total_bytes = bs * nb * world
     value = total_bytes * args.steps / elapsed_max / 2**30
@@ -704,6 +747,7 @@ def main():
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic (splitmix64 pattern filled on device)",
+        "full": args.full,
         "config": {"workload": desc, "block_size": bs, "nblocks_per_gpu": nb,
                    "bytes_per_gpu": bs * nb, "parallelism": f"shard{world} (contiguous block ranges, no collective)",
                    "kernel": path, "untimed_ramp_launches": nramp, "untimed_ramp_s": round(ramp_s, 2),
@@ -712,24 +756,27 @@ def main():
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": traffic, "kernel_ms": round(kernel_ms, 4),
-                     "alg_bytes_per_launch": alg_bytes, "kernel_launch_ms": lstats},
+                     "alg_bytes_per_launch": alg_bytes},
     }
+    if lstats:
+        result["roofline"]["kernel_launch_ms"] = lstats
     if roof:
         result["roofline"].update(roof)
         result["roofline"]["frac_of_measured"] = round(achieved / roof["measured_peak"], 4)
         result["roofline"]["frac_of_v0"] = round(achieved / roof["measured_peak_v0"], 4)
 
-    # the whole shard to host (untimed): every block is checked against the
-    # oracle, rank 0's first cpu-sample-bytes time the CPU baseline, and the
-    # streamed leg reads these same bytes from host memory
-    t_leg = time.perf_counter()
-    host = region.cpu().numpy()
-    gpu_crc = as_u32(out)
-    want = O.crc32_blocks(host, bs, nthreads=8)
-    head_ok = B.all_ok(bool(np.array_equal(gpu_crc, want)))
-    walls["parity"] = time.perf_counter() - t_leg
-    progress(rank, f"headline {value:.1f} GiB/s, parity {'ok' if head_ok else 'FAILED'}")
-    walked = region if args.config == "default" else None
+    if args.full:
+        # the whole shard to host (untimed): every block is checked against the
+        # oracle, rank 0's first cpu-sample-bytes time the CPU baseline, and the
+        # streamed leg reads these same bytes from host memory
+        t_leg = time.perf_counter()
+        host = region.cpu().numpy()
+        gpu_crc = as_u32(out)
+        want = O.crc32_blocks(host, bs, nthreads=8)
+        head_ok = B.all_ok(bool(np.array_equal(gpu_crc, want)))
+        walls["parity"] = time.perf_counter() - t_leg
+        progress(rank, f"headline {value:.1f} GiB/s, parity {'ok' if head_ok else 'FAILED'}")
+    walked = region if args.full and args.config == "default" else None
     shared = None if args.fresh_regions else walked  # the 4 GiB legs' blocks go into this region
     if walked is None:
         del region
@@ -755,20 +802,20 @@ def main():
             walls[label] = time.perf_counter() - t0
             progress(rank, f"{label} done in {walls[label]:.1f} s")
 
-    if not args.no_sweep and args.config == "default":
+    if args.full and not args.no_sweep and args.config == "default":
         result["sweep"] = {k: leg(f"sweep_{k}", resident_leg, B, name, args.sweep_steps, rotate=1 + i, shared=shared)
                            for i, (k, name) in enumerate(SWEEP)}
     # the odd sizes before the 128 GiB leg: a region allocated after that
     # leg's free read 5-6 % slower, its read roof too (0.78 against 0.83 on one
     # box, profiles/r06/odd/): the state the benchmark's own largest leg
     # leaves, not the kernel
-    if not args.no_odd and args.config == "default":
+    if args.full and not args.no_odd and args.config == "default":
         result["odd"] = {k: leg(f"odd_{k}", resident_leg, B, name, args.sweep_steps, parity="sampled", rotate=4 + i,
                                 shared=shared)
                          for i, (k, name) in enumerate(ODD)}
-    if not args.no_tib and args.config == "default":
+    if args.full and not args.no_tib and args.config == "default":
         result["tib"] = leg("tib", resident_leg, B, "tib", args.tib_steps, parity="sampled", rotate=3)
-    if not args.no_streamed:
+    if args.full and not args.no_streamed:
         result["streamed"] = leg("streamed", streamed_leg, B, host, bs, want)
     # cold passes LAST on the GPU: what a one-off recovery scrub sees (clock
     # ramp included); measured last so that the idle cannot leave its slower
@@ -785,14 +832,17 @@ def main():
     result["dist"] = {"backend": dist.get_backend() if world > 1 else None, "world_size": world,
                       "distinct_devices": len({(i["host"], i["pci"] or i["uuid"]) for i in infos}),
                       "rehearsal": rehearsal}
-    result["parity"] = {"checked_blocks_per_rank": nb, "sample": "every block", "bit_exact": head_ok,
-                        "oracle": "oracle/crc_oracle.c"}
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full:
+        result["parity"] = {"checked_blocks_per_rank": nb, "sample": "every block", "bit_exact": head_ok,
+                            "oracle": "oracle/crc_oracle.c"}
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         t_leg = time.perf_counter()
         nsamp = max(1, min(nb, args.cpu_sample_bytes // bs))
         result["cpu_baseline"], cpu_ok = cpu_baseline(O, host[: nsamp * bs], bs, gpu_crc[:nsamp])
         result["parity"]["bit_exact_vs_reference_build"] = cpu_ok
         walls["cpu_baseline"] = time.perf_counter() - t_leg
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, rank, world)
     t_leg = time.perf_counter()
     B.barrier()
     walls["final_barrier"] = time.perf_counter() - t_leg
@@ -801,15 +851,17 @@ def main():
         result["leg_wall_s"] = {k: round(v, 2) for k, v in walls.items()}
         result["leg_wall_s"]["note"] = ("rank 0's wall seconds per leg (process start to the line); the legs "
                                         "open and close with barriers, so rank 0's time is the job's")
-        detail = args.detail or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(result, f, indent=1)
-        except OSError as e:
-            detail = f"not written: {e}"
-        print(json.dumps(compact_line(result, os.path.relpath(detail, ROOT) if os.path.isabs(detail) else detail)),
-              flush=True)
+        detail = args.detail or (os.path.join(ROOT, "bench_out", "bench_detail.json") if args.full else None)
+        if detail is not None:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
+                with open(detail, "w") as f:
+                    json.dump(result, f, indent=1)
+            except OSError as e:
+                detail = f"not written: {e}"
+            if os.path.isabs(detail):
+                detail = os.path.relpath(detail, ROOT)
+        print(json.dumps(compact_line(result, detail)), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -46,10 +46,11 @@ def test_duplicate_devices():
 
 @pytest.mark.parametrize("local", ["0", "1"])
 def test_bench_exits_3_without_a_device_of_its_own(local):
-    """In this container no GPU is visible: every rank must stop with status
-    3 and say why, before any HIP call or collective."""
+    """With no GPU visible (none in the machine, or all hidden from the
+    child): every rank must stop with status 3 and say why, before any HIP
+    call or collective."""
     env = dict(os.environ, WORLD_SIZE="2", RANK=local, LOCAL_RANK=local, MASTER_ADDR="127.0.0.1",
-               MASTER_PORT="29533")
+               MASTER_PORT="29533", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     env.pop("PRISKV_BENCH_REHEARSAL", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env,
                        capture_output=True, text=True, timeout=300)
@@ -126,3 +127,91 @@ def test_compact_line_shows_every_leg_in_the_last_3000_chars():
     assert legs["tib"]["traffic"] == round(4303306084.03 / 4299161600, 4)
     assert legs["odd4095"]["frac_of_measured"] is None and legs["64KiB"]["bit_exact"] is True
     assert tail["cpu_baseline"]["cores"] == 1 and tail["cpu_baseline"]["multithread"]["threads"] == 16
+
+
+def test_plain_and_full_options():
+    """A plain run does the headline only; everything else sits behind --full."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.detail) == (7, 2, False, None, None)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_compact_line_of_a_plain_run():
+    """Without --full the line holds the contract's keys and the headline
+    roofline, and no leg, parity or detail entry."""
+    import json
+    full = {"metric": bench.METRIC, "value": 6342.07, "unit": "GiB/s", "n_gpus": 1, "steps": 20, "warmup": 5,
+            "ms_per_step": 0.63, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic", "full": False, "config": {"workload": "w", "block_size": 4096},
+            "roofline": {"bound": "hbm", "achieved": 6828.0, "peak": 8000.0, "unit": "GB/s", "frac": 0.8535,
+                         "traffic": None, "kernel_ms": 0.6296, "alg_bytes_per_launch": 4299161600},
+            "dist": {"backend": None, "world_size": 1, "distinct_devices": 1, "rehearsal": False}}
+    line = json.loads(json.dumps(bench.compact_line(full, None)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert line[k] == full[k], k
+    assert line["full"] is False and line["roofline"]["frac"] == 0.8535
+    for k in ("legs", "parity", "cpu_baseline", "detail"):
+        assert k not in line, k
+
+
+def test_dump_outputs_is_exact_and_bounded(tmp_path):
+    """--dump-outputs: every uint32 CRC survives the float64 file exactly; an
+    output beyond the 64 MB budget becomes the same seeded sample each time."""
+    import numpy as np
+    crc = np.array([0, 1, 0x2DFD2D88, 0x80000000, 0xFFFFFFFF], dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), crc, 0, 1)
+    got = np.load(tmp_path / "a" / "crc.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), crc)
+    assert not (tmp_path / "a" / "crc_index.npy").exists()
+    # a small budget stands in for 64 MB: 1000 CRCs against room for 34 (two 128 B headers, then CRC + index)
+    big = (np.arange(1000, dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32)
+    old, bench.DUMP_MAX_BYTES = bench.DUMP_MAX_BYTES, 800
+    try:
+        bench.dump_outputs(str(tmp_path / "b"), big, 0, 1)
+        bench.dump_outputs(str(tmp_path / "c"), big, 0, 1)
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    idx = np.load(tmp_path / "b" / "crc_index.npy").astype(np.int64)
+    val = np.load(tmp_path / "b" / "crc.npy")
+    assert idx.size == 34 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 1000
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 800
+    assert np.array_equal(val.astype(np.uint32), big[idx])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "crc_index.npy").astype(np.int64))
+    assert np.array_equal(val, np.load(tmp_path / "c" / "crc.npy"))
+    # several ranks share the budget and write a file each
+    bench.dump_outputs(str(tmp_path / "d"), crc, 3, 8)
+    assert np.array_equal(np.load(tmp_path / "d" / "crc_rank3.npy").astype(np.uint32), crc)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_the_timed_path_outputs(tmp_path):
+    """A plain run on a small shard: --steps sets the timed steps, the line
+    holds ms_per_step and no leg, and DIR/crc.npy holds the CRCs of the seeded
+    pattern, equal to the oracle's."""
+    import json
+
+    import numpy as np
+
+    import _oracle as O
+    nb = 4099
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--nblocks", str(nb), "--dump-outputs", str(tmp_path / "out")], capture_output=True,
+                       text=True, timeout=120, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["metric"] == bench.METRIC and line["unit"] == "GiB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["full"] is False
+    # value and ms_per_step describe the same steps (the line rounds them to 0.01 GiB/s and 0.0001 ms)
+    rel = 0.00006 / line["ms_per_step"] + 0.005 / line["value"] + 1e-6
+    assert abs(line["value"] - 4096 * nb / (line["ms_per_step"] * 1e-3) / 2**30) <= rel * line["value"]
+    for k in ("legs", "parity", "cpu_baseline", "detail"):
+        assert k not in line, k
+    assert os.listdir(tmp_path) == ["out"] and os.listdir(tmp_path / "out") == ["crc.npy"]
+    got = np.load(tmp_path / "out" / "crc.npy")
+    assert got.dtype == np.float64 and got.shape == (nb,)
+    want = O.crc32_blocks(O.fill_splitmix(4096 * nb, bench.SEED, 0), 4096)
+    assert np.array_equal(got.astype(np.uint32), want)

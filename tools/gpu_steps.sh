@@ -10,7 +10,7 @@
 #
 #   tests                 pytest -m gpu over every GPU test (+ smoke, C executables)
 #   tests:A,B             pytest -m gpu -k "A or B"
-#   bench[:A,B,...]       python bench.py A B ...  (commas stand for spaces)
+#   bench[:A,B,...]       python bench.py A B ...  (commas stand for spaces; --full for every leg)
 #   explore:BS:NB:R:F     tools/crc_explore BS NB R with EXPLORE_FILTER=F
 #   ranges:ARGS           tools/ranges_explore ARGS (commas for spaces)
 #   paths:ARGS            python tools/bench_paths.py ARGS (commas for spaces)

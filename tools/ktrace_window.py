@@ -26,7 +26,7 @@ def main():
     line = None
     with open(sys.argv[1]) as f:
         text = f.read()
-    try:  # bench.py's detail file (gpurun_out/bench_detail.json): one JSON document
+    try:  # bench.py's detail file (--detail; bench_out/bench_detail.json with --full): one JSON document
         line = json.loads(text)
     except ValueError:  # its stdout: the JSON line among other output
         for ln in text.splitlines():
