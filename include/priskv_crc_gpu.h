@@ -131,6 +131,57 @@ int priskv_crc32_verify_dev_bounded(const priskv_crc_ctx *ctx, const void *d_bas
                                     const uint32_t *d_lengths, uint64_t n, uint64_t max_len,
                                     const uint32_t *d_expected, uint64_t *d_status, void *stream);
 
+/* Gathered values.  A value on the client is an array of priskv_sgl {iova,
+ * length, mem} (client/priskv.h:74-78; priskv_get / priskv_set, :220-225) that
+ * the server reads or writes as the concatenation of the pieces
+ * (server/rdma.c:646-681).  The three calls below take n values as a flat
+ * list of parts plus d_value_first, n + 1 device entries: value v is parts
+ * d_value_first[v] .. d_value_first[v + 1] - 1, in order.
+ *   - Empty values: a value with no parts, or whose parts all have length 0,
+ *     has CRC 0 (priskv_crc32 of zero bytes: init 0, no final xor).
+ *   - Zero-length parts are legal anywhere in a value.
+ *   - A part may appear in several values and several times in one value, and
+ *     segments may overlap.
+ *   - Results are exact while a value's total length is below 2^48 bytes (the
+ *     range of the context's shift tables); suffix sums are 64-bit.
+ *   - d_value_first is a device array the host cannot check: the caller makes
+ *     it non-decreasing with d_value_first[n] <= nparts.  The kernels clamp
+ *     every index they derive from it to the part arrays, so a bad table gives
+ *     wrong CRCs for those values and never a read outside the part arrays.
+ *     Segment reads obey priskv_crc32_ranges_dev's contract: what the caller
+ *     describes is what is read, and nothing outside the segments is hashed.
+ *   - Every address is formed as 64-bit d_base + offset, so segments lying in
+ *     several allocations can be addressed from the lowest one's base.
+ *   - -EINVAL for a NULL ctx and for NULL arrays with n > 0 (the part arrays
+ *     may be NULL when there are no parts); n == 0 returns 0 without a launch,
+ *     except that the verify call still writes its status.
+ *
+ * out[v] = CRC of the concatenation of parts first[v] .. first[v+1]-1, given
+ * each part's own CRC and length.  No data bytes are read: with one CRC per
+ * KV page (priskv_crc32_blocks_dev over the page pool, once) the value CRC of
+ * any page list costs time in the page count, not the byte count. */
+int priskv_crc32_combine_dev(const priskv_crc_ctx *ctx, const uint32_t *d_part_crcs,
+                             const uint32_t *d_part_lengths, uint64_t nparts,
+                             const uint64_t *d_value_first /* n + 1 entries */, uint64_t n,
+                             uint32_t *d_out, void *stream);
+
+/* out[v] = priskv_crc32 of the concatenation, in order, of the segments
+ * d_base + d_seg_offsets[j], d_seg_lengths[j]   for j in first[v] .. first[v+1]-1.
+ * max_seg_len: host-known bound on the segment lengths, 0 = unknown; a launch hint
+ * only, exactly as priskv_crc32_ranges_dev_bounded's.  Needs nseg * 4 bytes of
+ * scratch besides priskv_crc32_ranges_dev's own. */
+int priskv_crc32_sgl_dev(const priskv_crc_ctx *ctx, const void *d_base, const uint64_t *d_seg_offsets,
+                         const uint32_t *d_seg_lengths, uint64_t nseg, const uint64_t *d_value_first,
+                         uint64_t n, uint64_t max_seg_len, uint32_t *d_out, void *stream);
+
+/* sgl_dev compared with d_expected[v]; d_status as priskv_crc32_verify_dev's
+ * ({mismatching values, smallest such v or UINT64_MAX}); a call with n = 0 still
+ * writes {0, UINT64_MAX}. */
+int priskv_crc32_sgl_verify_dev(const priskv_crc_ctx *ctx, const void *d_base, const uint64_t *d_seg_offsets,
+                                const uint32_t *d_seg_lengths, uint64_t nseg, const uint64_t *d_value_first,
+                                uint64_t n, uint64_t max_seg_len, const uint32_t *d_expected,
+                                uint64_t *d_status, void *stream);
+
 /* Host-resident per-value extents -- the memfile scrub at recovery
  * (server/kv.c:824-875 walks the keys; each live value is valuelen bytes at
  * value_off inside the value region, server/memory.h:50-51).  The kernel

@@ -54,6 +54,14 @@ SIGNATURES = [
     ("priskv_crc32_verify_dev_bounded", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_uint64, _C.c_uint64, _C.c_void_p, _C.c_void_p,
       _C.c_void_p]),
+    ("priskv_crc32_combine_dev", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_uint64, _C.c_void_p, _C.c_uint64, _C.c_void_p, _C.c_void_p]),
+    ("priskv_crc32_sgl_dev", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_uint64, _C.c_void_p, _C.c_uint64, _C.c_uint64,
+      _C.c_void_p, _C.c_void_p]),
+    ("priskv_crc32_sgl_verify_dev", _C.c_int,
+     [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_uint64, _C.c_void_p, _C.c_uint64, _C.c_uint64,
+      _C.c_void_p, _C.c_void_p, _C.c_void_p]),
     ("priskv_crc32_blocks_host", _C.c_int,
      [_C.c_void_p, _C.c_void_p, _C.c_uint64, _C.c_uint32, _C.c_void_p]),
     ("priskv_crc32_ranges_host", _C.c_int,
@@ -288,6 +296,79 @@ class CrcContext:
                "priskv_crc32_verify_dev")
         return status
 
+    # ---- gathered values (a priskv_sgl[] per value)
+    def combine_dev(self, part_crcs, part_lengths, value_first, out=None, stream=None):
+        """priskv_crc32_combine_dev: out[v] = CRC of the concatenation of parts
+        value_first[v] .. value_first[v + 1] - 1 from each part's own CRC and
+        length (no data bytes are read).  part_crcs: 4-byte, part_lengths:
+        int32, value_first: int64 with n + 1 entries, all on one device."""
+        import torch
+        nparts = part_crcs.numel()
+        if (part_lengths.numel() != nparts or part_crcs.element_size() != 4 or part_lengths.dtype != torch.int32
+                or value_first.dtype != torch.int64 or value_first.numel() < 1):
+            raise ValueError("part_crcs 4-byte and part_lengths int32 device tensors of equal length, "
+                             "value_first int64 with n + 1 entries")
+        n = value_first.numel() - 1
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=value_first.device)
+        if out.numel() < n or out.element_size() != 4:
+            raise ValueError("out must be a 4-byte tensor of >= len(value_first) - 1 entries")
+        _device_args(value_first, part_crcs, part_lengths, out)
+        if not value_first.is_contiguous():
+            raise ValueError("value_first must be contiguous")
+        _check(lib().priskv_crc32_combine_dev(self._h, part_crcs.data_ptr(), part_lengths.data_ptr(), nparts,
+                                              value_first.data_ptr(), n, out.data_ptr(), _stream_ptr(stream)),
+               "priskv_crc32_combine_dev")
+        return out
+
+    @staticmethod
+    def _sgl_args(region, seg_offsets, seg_lengths, value_first):
+        import torch
+        nseg = seg_offsets.numel()
+        if (seg_lengths.numel() != nseg or seg_offsets.dtype != torch.int64 or seg_lengths.dtype != torch.int32
+                or value_first.dtype != torch.int64 or value_first.numel() < 1):
+            raise ValueError("seg_offsets int64 and seg_lengths int32 device tensors of equal length, "
+                             "value_first int64 with n + 1 entries")
+        return nseg, value_first.numel() - 1
+
+    def sgl_dev(self, region, seg_offsets, seg_lengths, value_first, out=None, stream=None, max_seg_len=None):
+        """priskv_crc32_sgl_dev: out[v] = priskv_crc32 of the concatenation of
+        the segments region + seg_offsets[j], seg_lengths[j] for j in
+        value_first[v] .. value_first[v + 1] - 1 (pack_sgl builds the three
+        arrays).  max_seg_len: a host-known bound on the segment lengths, a
+        launch hint only."""
+        import torch
+        nseg, n = self._sgl_args(region, seg_offsets, seg_lengths, value_first)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=region.device)
+        if out.numel() < n or out.element_size() != 4:
+            raise ValueError("out must be a 4-byte tensor of >= len(value_first) - 1 entries")
+        _device_args(region, seg_offsets, seg_lengths, value_first, out)
+        _check(lib().priskv_crc32_sgl_dev(self._h, region.data_ptr(), seg_offsets.data_ptr(), seg_lengths.data_ptr(),
+                                          nseg, value_first.data_ptr(), n, int(max_seg_len or 0), out.data_ptr(),
+                                          _stream_ptr(stream)), "priskv_crc32_sgl_dev")
+        return out
+
+    def sgl_verify_dev(self, region, seg_offsets, seg_lengths, value_first, expected, status=None, stream=None,
+                       max_seg_len=None):
+        """priskv_crc32_sgl_verify_dev: sgl_dev compared with expected on the
+        device; returns the 2-entry int64 status tensor {mismatching values,
+        smallest such value or -1 (UINT64_MAX)}, as verify_dev's."""
+        import torch
+        nseg, n = self._sgl_args(region, seg_offsets, seg_lengths, value_first)
+        if expected.numel() != n or expected.element_size() != 4:
+            raise ValueError("expected must be a 4-byte device tensor of len(value_first) - 1 entries")
+        if status is None:
+            status = torch.empty(2, dtype=torch.int64, device=region.device)
+        if status.numel() < 2 or status.element_size() != 8:
+            raise ValueError("status must be an 8-byte tensor of >= 2 entries")
+        _device_args(region, seg_offsets, seg_lengths, value_first, expected, status)
+        _check(lib().priskv_crc32_sgl_verify_dev(self._h, region.data_ptr(), seg_offsets.data_ptr(),
+                                                 seg_lengths.data_ptr(), nseg, value_first.data_ptr(), n,
+                                                 int(max_seg_len or 0), expected.data_ptr(), status.data_ptr(),
+                                                 _stream_ptr(stream)), "priskv_crc32_sgl_verify_dev")
+        return status
+
     def fill_splitmix(self, region, seed: int, word_offset: int = 0, stream=None, nbytes=None) -> None:
         size = region.numel() * region.element_size()
         nb = size if nbytes is None else nbytes
@@ -410,6 +491,25 @@ class CrcBatcher:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def pack_sgl(values):
+    """A list of values, each a list of (offset, length) pairs -- one pair per
+    priskv_sgl entry, offset = iova minus the chosen base -- as the three
+    arrays of the gathered-value calls: (seg_offsets uint64[nseg],
+    seg_lengths uint32[nseg], value_first uint64[n + 1])."""
+    offs, lens, first = [], [], [0]
+    for v in values:
+        for off, ln in v:
+            off, ln = int(off), int(ln)
+            if off < 0 or off >= 2**64:
+                raise ValueError(f"segment offset {off} is not a uint64")
+            if ln < 0 or ln >= 2**32:
+                raise ValueError(f"segment length {ln} is not a uint32 (priskv_sgl.length)")
+            offs.append(off)
+            lens.append(ln)
+        first.append(len(offs))
+    return (np.array(offs, dtype=np.uint64), np.array(lens, dtype=np.uint32), np.array(first, dtype=np.uint64))
 
 
 def as_u32(t) -> np.ndarray:

@@ -3194,6 +3194,144 @@ __global__ __launch_bounds__(256) void crc_verify_kernel(const uint32_t *__restr
 }
 
 // ---------------------------------------------------------------------------
+// Gathered values (priskv_crc32_combine_dev / _sgl_dev): out[v] = XOR over the
+// value's parts j of Z_(s_j)(crc_j), s_j = the bytes after part j in the value
+// (the identity above; crc(empty) = 0, so empty values and zero-length parts
+// need no case of their own).  The shift amounts differ per part and are
+// known only here, so unlike zshift_lds (a wave-uniform amount, the wave's
+// lanes holding one matrix's columns) every LANE shifts its own part: one
+// apply of Z_(2^b) per set bit b of s, each as 8 nibble lookups in LDS
+// (znib[b][k][v] = Z_(2^b) of nibble k holding v: 48 x 8 x 16 words, 24 KiB,
+// built by the host from the columns d_zpow holds) XORed together.  A lane whose
+// part CRC is 0 or whose s is 0 looks nothing up; a wave takes as many
+// applies as the largest popcount(s) among its lanes.  (A 32-step GF(2)[x]
+// multiply by x^(8 2^b) per set bit needs 192 B of tables instead and ~160
+// VALU instructions per apply against ~25 here: measured 18 against 9 us
+// for 512 Ki parts, DESIGN section 11.)
+//
+// G lanes per value (G = 1 .. 64, chosen by the host from nparts / n): 64 / G
+// values per wave.  A group walks its value's parts from the last to the
+// first, G at a time, lane g on part hi - 1 - g, so that an inclusive 64-bit
+// scan over the group's lanes is the suffix sum of the lengths; the group's
+// total carries into the next G parts.  Values of more than kCombLong * G
+// parts are left to the whole wave, one after the other with all 64 lanes
+// (one value of many parts among values of few).
+//
+// value_first is a device table the host cannot check: every index derived
+// from it is clamped to [0, nparts], and a range that runs backwards is
+// empty, so a bad table gives wrong CRCs and never a read outside the part
+// arrays.  Shift amounts are taken mod 2^48 (the rows of znib).
+// expected != nullptr: compare instead of (or besides) storing, with the
+// status protocol of crc_verify_kernel.
+// ---------------------------------------------------------------------------
+constexpr int kCombThreads = 256;
+constexpr int kCombRows = 48;    // = crc_gpu.hip kZpowRows: Z_(2^b), b < 48
+constexpr int kCombRowWords = 8 * 16; // one row: 8 nibbles x 16 values
+constexpr uint32_t kCombLong = 8; // a group takes values of up to kCombLong * G parts itself
+
+// Z_s(c) for this lane's own c and s (znib in LDS)
+__device__ __forceinline__ uint32_t nib_shift(uint32_t c, uint64_t s, const uint32_t *znib)
+{
+    s = c ? (s & ((1ull << kCombRows) - 1)) : 0;
+#pragma unroll 1
+    while (s) {
+        const uint32_t *t = znib + __builtin_ctzll(s) * kCombRowWords;
+        uint32_t r[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            r[k] = t[k * 16 + ((c >> (4 * k)) & 15u)];
+        const uint32_t p = __builtin_amdgcn_bitop3_b32(r[0], r[1], r[2], 0x96);
+        const uint32_t q = __builtin_amdgcn_bitop3_b32(r[3], r[4], r[5], 0x96);
+        c = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(p, q, r[6], 0x96), r[7], 0u, 0x96);
+        s &= s - 1;
+    }
+    return c;
+}
+
+// the parts [a, b) of one value by the W lanes of a group (w = lane in group):
+// every lane of the group returns the value's CRC
+template <int W>
+__device__ __forceinline__ uint32_t comb_span(const uint32_t *__restrict__ crcs, const uint32_t *__restrict__ lens,
+                                              uint64_t a, uint64_t b, int w, const uint32_t *znib)
+{
+    uint32_t acc = 0;
+    uint64_t tail = 0; // bytes after the parts still to come
+    for (uint64_t hi = b; hi > a; hi = hi - a > W ? hi - W : a) {
+        const bool mine = hi - a > (uint64_t)w;
+        const uint64_t j = hi - 1 - (uint64_t)w;
+        const uint32_t len = mine ? lens[j] : 0u;
+        const uint32_t c = mine ? crcs[j] : 0u;
+        uint64_t incl = len;
+#pragma unroll
+        for (int d = 1; d < W; d <<= 1) {
+            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, d, W);
+            const uint32_t up = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), d, W);
+            if (w >= d)
+                incl += ((uint64_t)up << 32) | lo;
+        }
+        acc ^= nib_shift(c, tail + incl - len, znib);
+        if (W > 1) {
+            const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)incl, W - 1, W);
+            const uint32_t up = (uint32_t)__shfl((int)(uint32_t)(incl >> 32), W - 1, W);
+            tail += ((uint64_t)up << 32) | lo;
+        } else {
+            tail += incl;
+        }
+    }
+    return group_xor<W>(acc);
+}
+
+template <int G>
+__global__ __launch_bounds__(kCombThreads) void crc_combine_parts_kernel(
+    const uint32_t *__restrict__ crcs, const uint32_t *__restrict__ lens, uint64_t nparts,
+    const uint64_t *__restrict__ first, uint64_t n, const uint32_t *__restrict__ znib_g, uint32_t *__restrict__ out,
+    const uint32_t *__restrict__ expected, unsigned long long *__restrict__ status)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t znib[kCombRows * kCombRowWords];
+    copy_to_lds(znib_g, znib, kCombRows * kCombRowWords / 4);
+    lds_dma_landed();
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int w = lane & (G - 1);
+    constexpr uint64_t kPerWg = kCombThreads / G; // values per workgroup and pass
+    // every lane of a wave runs the same number of passes (base is uniform)
+    for (uint64_t base = (uint64_t)blockIdx.x * kPerWg; base < n; base += (uint64_t)gridDim.x * kPerWg) {
+        const uint64_t v = base + threadIdx.x / G;
+        uint64_t a = 0, b = 0;
+        if (v < n) {
+            a = first[v];
+            b = first[v + 1];
+            a = a < nparts ? a : nparts;
+            b = b < nparts ? b : nparts;
+            b = b < a ? a : b;
+        }
+        const bool far = G < 64 && b - a > (uint64_t)kCombLong * G;
+        uint32_t crc = comb_span<G>(crcs, lens, a, far ? a : b, w, znib);
+        if (G < 64) {
+            uint64_t m = __ballot(far && w == 0);
+            while (m) { // wave-uniform
+                const int l = __builtin_ctzll(m);
+                m &= m - 1;
+                const uint32_t c = comb_span<64>(crcs, lens, readlane64(a, l), readlane64(b, l), lane, znib);
+                if ((lane & ~(G - 1)) == l)
+                    crc = c;
+            }
+        }
+        const bool lead = v < n && w == 0;
+        if (lead && out)
+            out[v] = crc;
+        if (expected) {
+            const uint64_t bad = __ballot(lead && crc != expected[v]);
+            if (bad && lane == 0) {
+                atomicAdd(&status[0], (unsigned long long)__popcll(bad));
+                atomicMin(&status[1],
+                          (unsigned long long)(base + (uint64_t)((threadIdx.x & ~63u) + __ffsll((long long)bad) - 1) / G));
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // XCD dispatch probe (once per context): workgroup b records the XCD (XCC)
 // it runs on.  The rows kernel's XCD weights assume round-robin dispatch,
 // workgroup b on XCD (b + k) % 8 with k the queue's first XCD (read per launch

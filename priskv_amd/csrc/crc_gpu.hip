@@ -91,6 +91,7 @@ struct priskv_crc_ctx {
     uint32_t *d_small_img[5];  // sub-KiB byte-fold images for G = 1 << j, j = 1..4 (prv_small_image)
     uint32_t *d_sarwate;       // 256 words
     uint32_t *d_zpow;          // kZpowRows x 32 words: columns of Z_(2^k) (segment combine)
+    uint32_t *d_znib;          // kCombRows x 8 x 16 words: nibble tables of Z_(2^k) (crc_combine_parts_kernel)
     uint32_t *d_rowshift;      // 16 x 4 x 32 words: columns of Z_-p o Z_(256(3-k)) (extents fold)
     uint32_t *d_winimg;        // window mode images for W = 4, 8, 12, 16 KiB (crc_device.inc s_winimg)
     // host-streamed path (guarded by lock)
@@ -684,6 +685,41 @@ int launch_extents(const priskv_crc_ctx *ctx, const uint8_t *base, uint64_t n, c
     }
     return launch_ext_kernel(ctx, false, many, false, s, abase, n, offs, lens, shift, stride, len_const, out, nullptr,
                              nullptr, nullptr, nullptr);
+}
+
+// ---- gathered values: the parts' CRCs combined per value ------------------------
+static_assert(kCombRows == kZpowRows, "one nibble table per Z_(2^b) row: totals below 2^48 bytes");
+constexpr int kCombWgPerCu = 4; // grid cap of the combine kernel: 16 waves per CU
+
+template <int G>
+int launch_combine_g(const priskv_crc_ctx *ctx, const uint32_t *crcs, const uint32_t *lens, uint64_t nparts,
+                     const uint64_t *first, uint64_t n, uint32_t *out, const uint32_t *expected, uint64_t *status,
+                     hipStream_t s)
+{
+    const uint64_t per_wg = kCombThreads / G, cap = (uint64_t)ctx->num_cus * kCombWgPerCu;
+    const uint64_t want = (n + per_wg - 1) / per_wg;
+    return launch_k(crc_combine_parts_kernel<G>, dim3((uint32_t)(want < cap ? want : cap)), dim3(kCombThreads), s,
+                    crcs, lens, nparts, first, n, ctx->d_znib, out, expected, (unsigned long long *)status);
+}
+
+// G lanes per value: the power of two at or above the mean part count (the
+// counts are device data; a value far above the mean gets its whole wave)
+int launch_combine(const priskv_crc_ctx *ctx, const uint32_t *crcs, const uint32_t *lens, uint64_t nparts,
+                   const uint64_t *first, uint64_t n, uint32_t *out, const uint32_t *expected, uint64_t *status,
+                   hipStream_t s)
+{
+    const uint64_t mean = (nparts + n - 1) / n;
+#define PRV_COMB(G)                                                                                                  \
+    if (mean <= G)                                                                                                   \
+    return launch_combine_g<G>(ctx, crcs, lens, nparts, first, n, out, expected, status, s)
+    PRV_COMB(1);
+    PRV_COMB(2);
+    PRV_COMB(4);
+    PRV_COMB(8);
+    PRV_COMB(16);
+    PRV_COMB(32);
+#undef PRV_COMB
+    return launch_combine_g<64>(ctx, crcs, lens, nparts, first, n, out, expected, status, s);
 }
 
 // ---- rows kernel plans --------------------------------------------------------
@@ -1892,6 +1928,24 @@ int priskv_crc_ctx_create(int device, priskv_crc_ctx **out)
         prv_shift_columns(h_img + k * 32, 1ull << k);
     if ((rc = herr(hipMemcpy(c->d_zpow, h_img, sizeof(uint32_t) * kZpowRows * 32, hipMemcpyHostToDevice))))
         goto fail;
+    // the same matrices as nibble tables: word (k, nb, v) = Z_(2^k) of nibble nb holding v
+    static_assert(kCombRows * kCombRowWords + kZpowRows * 32 <= PRV_LDS_WORDS, "both fit the staging buffer");
+    {
+        uint32_t *zn = h_img + kZpowRows * 32;
+        for (int k = 0; k < kCombRows; k++)
+            for (int nb = 0; nb < 8; nb++)
+                for (uint32_t v = 0; v < 16; v++) {
+                    uint32_t r = 0;
+                    for (int bit = 0; bit < 4; bit++)
+                        if ((v >> bit) & 1u)
+                            r ^= h_img[k * 32 + 4 * nb + bit];
+                    zn[(k * 8 + nb) * 16 + (int)v] = r;
+                }
+        if ((rc = herr(hipMalloc((void **)&c->d_znib, sizeof(uint32_t) * kCombRows * kCombRowWords))) ||
+            (rc = herr(hipMemcpy(c->d_znib, zn, sizeof(uint32_t) * kCombRows * kCombRowWords,
+                                 hipMemcpyHostToDevice))))
+            goto fail;
+    }
     for (int gi = 0; gi < 3; gi++) {
         const uint32_t G = 64u >> gi; // 64, 32, 16
         prv_lds_image(h_img, 16u * G - 16u);
@@ -1970,6 +2024,7 @@ void priskv_crc_ctx_destroy(priskv_crc_ctx *c)
     (void)hipFree(c->d_rowshift);
     (void)hipFree(c->d_winimg);
     (void)hipFree(c->d_zpow);
+    (void)hipFree(c->d_znib);
     (void)hipFree(c->d_scrub);
     {
         // the slots' last uses are on their home streams, which may be gone
@@ -2177,6 +2232,85 @@ int priskv_crc32_verify_dev_bounded(const priskv_crc_ctx *ctx, const void *d_bas
 {
     return verify_dev(ctx, d_base, d_offsets, d_lengths, n, d_expected, d_status, stream,
                       max_len < 0xFFFFFFFFull ? max_len : 0xFFFFFFFFull);
+}
+
+// ---- gathered values: parts combined on the device ---------------------------
+namespace {
+// sgl_dev (d_expected == nullptr) and sgl_verify_dev (d_out == nullptr): the
+// segments' CRCs through launch_extents into pooled scratch, then the combine
+int sgl_dev(const priskv_crc_ctx *ctx, const void *d_base, const uint64_t *d_seg_offsets,
+            const uint32_t *d_seg_lengths, uint64_t nseg, const uint64_t *d_value_first, uint64_t n,
+            uint64_t max_seg_len, uint32_t *d_out, const uint32_t *d_expected, uint64_t *d_status, hipStream_t s)
+{
+    if (nseg == 0) // every value is empty
+        return launch_combine(ctx, nullptr, nullptr, 0, d_value_first, n, d_out, d_expected, d_status, s);
+    Scratch sc(ctx, s);
+    if (int rc = sc.get(nseg * sizeof(uint32_t)))
+        return rc;
+    uint32_t *part = static_cast<uint32_t *>(sc.p);
+    int rc = launch_extents(ctx, (const uint8_t *)d_base, nseg, d_seg_offsets, d_seg_lengths, 0, 0, part, s,
+                            max_seg_len < 0xFFFFFFFFull ? max_seg_len : 0xFFFFFFFFull);
+    if (!rc)
+        rc = launch_combine(ctx, part, d_seg_lengths, nseg, d_value_first, n, d_out, d_expected, d_status, s);
+    const int frc = sc.release();
+    return rc ? rc : frc;
+}
+} // namespace
+
+int priskv_crc32_combine_dev(const priskv_crc_ctx *ctx, const uint32_t *d_part_crcs, const uint32_t *d_part_lengths,
+                             uint64_t nparts, const uint64_t *d_value_first, uint64_t n, uint32_t *d_out,
+                             void *stream)
+{
+    if (!ctx)
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!d_value_first || !d_out || (nparts && (!d_part_crcs || !d_part_lengths)))
+        return -EINVAL;
+    DevGuard g(ctx->device);
+    if (!g.ok)
+        return -ENODEV;
+    return launch_combine(ctx, d_part_crcs, d_part_lengths, nparts, d_value_first, n, d_out, nullptr, nullptr,
+                          (hipStream_t)stream);
+}
+
+int priskv_crc32_sgl_dev(const priskv_crc_ctx *ctx, const void *d_base, const uint64_t *d_seg_offsets,
+                         const uint32_t *d_seg_lengths, uint64_t nseg, const uint64_t *d_value_first, uint64_t n,
+                         uint64_t max_seg_len, uint32_t *d_out, void *stream)
+{
+    if (!ctx)
+        return -EINVAL;
+    if (n == 0)
+        return 0;
+    if (!d_value_first || !d_out || (nseg && (!d_base || !d_seg_offsets || !d_seg_lengths)))
+        return -EINVAL;
+    DevGuard g(ctx->device);
+    if (!g.ok)
+        return -ENODEV;
+    return sgl_dev(ctx, d_base, d_seg_offsets, d_seg_lengths, nseg, d_value_first, n, max_seg_len, d_out, nullptr,
+                   nullptr, (hipStream_t)stream);
+}
+
+int priskv_crc32_sgl_verify_dev(const priskv_crc_ctx *ctx, const void *d_base, const uint64_t *d_seg_offsets,
+                                const uint32_t *d_seg_lengths, uint64_t nseg, const uint64_t *d_value_first,
+                                uint64_t n, uint64_t max_seg_len, const uint32_t *d_expected, uint64_t *d_status,
+                                void *stream)
+{
+    if (!ctx || !d_status)
+        return -EINVAL;
+    if (n && (!d_value_first || !d_expected || (nseg && (!d_base || !d_seg_offsets || !d_seg_lengths))))
+        return -EINVAL;
+    DevGuard g(ctx->device);
+    if (!g.ok)
+        return -ENODEV;
+    hipStream_t s = (hipStream_t)stream;
+    // status first: a zero-length verify still reports {0, UINT64_MAX}
+    if (int rc = launch_k(crc_status_init_kernel, dim3(1), dim3(64), s, (unsigned long long *)d_status))
+        return rc;
+    if (n == 0)
+        return 0;
+    return sgl_dev(ctx, d_base, d_seg_offsets, d_seg_lengths, nseg, d_value_first, n, max_seg_len, nullptr,
+                   d_expected, d_status, s);
 }
 
 int priskv_crc_fill_splitmix_dev(const priskv_crc_ctx *ctx, void *d_dst, uint64_t nbytes, uint64_t seed,
